@@ -10,7 +10,10 @@ micro-batches of 32) through the whole hot path: dual ViT (DINOv2-L/14-reg4
 decode steps (hipGraph replay) per micro-batch, then one all-gather of the
 generated tokens (RCCL on N > 1).  Tokens per step = 256 * (256+64+32).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W]       (the headline only)
+  python bench.py --full ...           (+ per-kernel timing pass, isolated
+                                        rooflines, CPU baseline, C3's serving pass)
+  python bench.py --dump-outputs DIR   (the last timed step's outputs as .npy)
   torchrun --nproc-per-node N bench.py --gpus N ...     (one rank per GPU)
   python bench.py --config c2|c3|c4                      (the other configs)
 
@@ -108,9 +111,22 @@ def parse(argv=None):
   ap.add_argument("--image-size", type=int)
   ap.add_argument("--prompt", type=int)
   ap.add_argument("--decode", type=int)
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="besides the headline pass: a second pass of the same "
+                  "K steps with per-kernel HIP events (kernels, roofline*), "
+                  "the isolated roofline launches, the CPU baseline and, for "
+                  "C3, the serving pass; a plain run sets up, warms up, times "
+                  "the K steps and prints the line with those fields null")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="after the timed steps, write what the last timed step "
+                  "returned (the gathered rows of every sample) as "
+                  "DIR/<name>.npy, float32 (rank 0)")
+  ap.add_argument("--no-cpu-baseline", action="store_true",
+                  help="with --full: skip the CPU baseline")
   ap.add_argument("--cpu-decode-steps", type=int)
-  ap.add_argument("--no-kernel-timing", action="store_true")
+  ap.add_argument("--no-kernel-timing", action="store_true",
+                  help="with --full: skip the per-kernel timing pass and the "
+                  "isolated roofline launches")
   ap.add_argument("--text-only", action="store_true", default=None,
                   help="C2-style text-only run (no vision tower)")
   ap.add_argument("--no-pipeline", action="store_true",
@@ -133,8 +149,8 @@ def parse(argv=None):
                   help="after the headline pass, time K more steps with the "
                   "lanes carried across steps (a serving loop: step i + 1's "
                   "prefill overlaps step i's decode) and report them as "
-                  "value_serving; on by default for C3, whose value is the "
-                  "single-request rate")
+                  "value_serving; on by default for C3 under --full (C3's "
+                  "value is the single-request rate)")
   ap.add_argument("--rehearsal", choices=["cpu"], default=None,
                   help="no GPU: the launch / sharding / input generation / "
                   "gather / max-over-ranks path of the bench over gloo with a "
@@ -146,8 +162,15 @@ def parse(argv=None):
       setattr(args, k, v)
   if args.cpu_decode_steps is None:
     args.cpu_decode_steps = args.decode
+  # C3's value is one request at a time with or without --full; only the
+  # extra serving pass itself is --full's
+  args.single_request = bool(args.serving_pass) or (
+      args.serving_pass is None and args.config == "c3")
   if args.serving_pass is None:
-    args.serving_pass = args.config == "c3"
+    args.serving_pass = args.full and args.config == "c3"
+  # the second pass, the isolated launches and the CPU baseline are --full's
+  args.kernel_timing = args.full and not args.no_kernel_timing
+  args.cpu_baseline = args.full and not args.no_cpu_baseline
   return args
 
 
@@ -496,6 +519,8 @@ def rehearse(args):
   agg, per = prefill_rates(mb, n_vis + args.prompt, D.max_over_ranks(tp) * 1e3 + 1e-6,
                            world)
   tok_per_step = gb * (n_vis + args.prompt + args.decode)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, out, args.decode)
   if rank == 0:
     print(json.dumps({
         "metric": "rehearsal (CPU, no model): " + METRIC, "n_gpus": world,
@@ -514,6 +539,21 @@ def rehearse(args):
         "gathered_rows": int(out.shape[0])}), flush=True)
   D.barrier()
   D.shutdown()
+
+
+def dump_outputs(path, out, decode):
+  """--dump-outputs: what the last timed step returned to its caller -- the
+  gathered rows of every sample of the global batch, [global batch, decode]
+  generated token ids (with --decode 0, C4, the [global batch, 1] cache
+  probe the prefill-only step returns) -- as one float32 .npy (token ids are
+  below 2^24, so exact).  The inputs and weights are seeded, so two builds
+  run with the same arguments are comparable row for row."""
+  import numpy as np
+  os.makedirs(path, exist_ok=True)
+  name = "generated_tokens" if decode else "prefill_cache_probe"
+  arr = out.detach().to("cpu", torch.float32).contiguous().numpy()
+  assert arr.nbytes <= 64 << 20, arr.nbytes
+  np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def fail_fast(exc: BaseException) -> None:
@@ -586,7 +626,7 @@ def run(args):
   # config: its value is one request at a time, the two-requests-in-flight
   # rate goes to value_serving (--serving-pass)
   can_continue = bool(args.decode and not args.no_pipeline and n_micro == 1)
-  continuous = can_continue and not args.no_continuous and not args.serving_pass
+  continuous = can_continue and not args.no_continuous and not args.single_request
   mb = micro[0].stop - micro[0].start          # samples per micro-batch
   tok_cpu, img_cpu = make_inputs(gb, lo, hi, args.image_size, args.prompt,
                                  cfg.vocab_size, args.text_only)
@@ -753,9 +793,11 @@ def run(args):
     # ~3 % of the step); a second pass of the same K steps times the kernels
     dt, step_ev, ev_list, out = timed_pass(False)
     host_ms = host_enqueue["s"] * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+      dump_outputs(args.dump_outputs, out, args.decode)
     ksum = {}
     pipelined = bool(args.decode and not args.no_pipeline and (n_micro > 1 or continuous))
-    if not args.no_kernel_timing:
+    if args.kernel_timing:
       _, _, ev_seq, _ = timed_pass(True)
       ksum = ops.TIMER.summary()
       # with two lanes in flight the headline pass's prefill / decode event
@@ -783,11 +825,11 @@ def run(args):
       decode_ms.append(ev["decode_start"].elapsed_time(ev["decode_end"])
                        / ev["decode_steps"])
   vit_iso = (vit_attention_isolated(vis, args.batch, dev)
-             if vis is not None and rank == 0 and not args.no_kernel_timing else None)
+             if vis is not None and rank == 0 and args.kernel_timing else None)
   img_iso = (image_preprocess_isolated(args.batch, args.image_size, dev)
-             if vis is not None and rank == 0 and not args.no_kernel_timing else None)
+             if vis is not None and rank == 0 and args.kernel_timing else None)
   scan_iso = None
-  if (rank == 0 and not args.no_kernel_timing and not any(
+  if (rank == 0 and args.kernel_timing and not any(
       k in ksum for k in ("rnn_scan_kernel", "rnn_scan_chunk_kernel"))):
     scan_iso = scan_isolated(mb, n_vis + args.prompt - (1 if args.decode else 0),
                              cfg.lru_width, dev)
@@ -875,7 +917,7 @@ def run(args):
         "prefill_ms": round(pre_ms, 3),
         "prefill_timing": (("last micro-batch's prefill in the kernel-timing pass "
                             "(micro-batches run one after another)"
-                            if not args.no_kernel_timing else
+                            if args.kernel_timing else
                             "last micro-batch's prefill, overlapping the previous "
                             "micro-batch's decode (Sampler.generate_many)")
                            if args.decode and not args.no_pipeline and
@@ -919,13 +961,16 @@ def run(args):
                         "est_ms_per_step": round(v["total_ms"] * ops.TIMER.sample /
                                                  args.steps, 3)}
                     for k, v in sorted(ksum.items())},
-        "kernel_timing": f"HIP events on a seeded 1/{ops.TIMER.sample} of the launches "
-                         "of a second timed pass of the same K steps, micro-batches "
-                         "run one after another (the value / ms_per_step pass "
-                         "carries no per-kernel events: they cost the stream ~3 % "
-                         "of the step; it runs two micro-batch lanes whose kernels "
-                         "share the CUs, so an event pair there would time "
-                         "queueing behind the other lane)",
+        "kernel_timing": (f"HIP events on a seeded 1/{ops.TIMER.sample} of the launches "
+                          "of a second timed pass of the same K steps, micro-batches "
+                          "run one after another (the value / ms_per_step pass "
+                          "carries no per-kernel events: they cost the stream ~3 % "
+                          "of the step; it runs two micro-batch lanes whose kernels "
+                          "share the CUs, so an event pair there would time "
+                          "queueing behind the other lane)"
+                          if args.kernel_timing else
+                          "none (the per-kernel pass runs under --full)"),
+        "full": args.full,
         "generated_tokens_checksum": int(out.long().sum().item()),
     }
     if serving is not None:
@@ -935,7 +980,7 @@ def run(args):
           "the same K steps with the two lanes carried across steps (a serving "
           "loop: step i + 1's request prefills while step i's decodes; two "
           "requests in flight); value is one request at a time")
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.cpu_baseline:
       result["cpu_baseline"] = cpu_baseline(model, cfg, vis, tok_cpu, img_cpu,
                                             args.cpu_decode_steps)
     else:

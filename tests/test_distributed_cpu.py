@@ -230,6 +230,46 @@ def test_bench_self_spawn_world2_gloo():
     assert line["definitions"]["version"] >= 6
 
 
+def test_bench_dump_outputs_rehearsal(tmp_path):
+  """--dump-outputs DIR writes the last step's gathered rows as one float32
+  .npy (the CPU rehearsal's rows here): every sample's row, the values the
+  line's checksum sums, and exactly `--steps` timed steps."""
+  import numpy as np
+  line, _ = _run_bench("--gpus", "1", "--rehearsal", "cpu", "--global-batch", "8",
+                       "--batch", "2", "--image-size", "28", "--prompt", "6",
+                       "--decode", "3", "--steps", "3", "--warmup", "0",
+                       "--dump-outputs", str(tmp_path / "dump"))
+  assert line["steps"] == 3
+  files = sorted(os.listdir(tmp_path / "dump"))
+  assert files == ["generated_tokens.npy"]
+  a = np.load(tmp_path / "dump" / files[0])
+  assert a.dtype == np.float32 and a.shape == (8, 3)
+  assert int(a.astype(np.int64).sum()) == line["generated_tokens_checksum"]
+  import bench
+  tok, img = bench.make_inputs(8, 0, 8, 28, 6, 256000, False)
+  want = bench.rehearsal_rows(tok, img, 3, 256000)
+  assert np.array_equal(a, want.numpy().astype(np.float32))
+
+
+def test_bench_plain_and_full_arguments():
+  """A plain run asks for no pass beyond the headline's; --full turns the
+  per-kernel pass, the CPU baseline and C3's serving pass on, and the
+  --no-* switches still take each of them out."""
+  import bench
+  a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+  assert (a.steps, a.warmup) == (7, 3)
+  assert not (a.full or a.kernel_timing or a.cpu_baseline or a.serving_pass)
+  assert a.dump_outputs is None
+  # C3's value stays the single-request rate; only the extra pass is --full's
+  c3 = bench.parse(["--config", "c3"])
+  assert c3.single_request and not c3.serving_pass and not a.single_request
+  f = bench.parse(["--full"])
+  assert f.kernel_timing and f.cpu_baseline and not f.serving_pass
+  assert bench.parse(["--full", "--config", "c3"]).serving_pass
+  g = bench.parse(["--full", "--no-cpu-baseline", "--no-kernel-timing"])
+  assert not g.kernel_timing and not g.cpu_baseline
+
+
 def test_bench_rank_failure_exits_nonzero():
   """Fail-fast: a rank that raises (here: a global batch the ranks cannot
   split) tears its group down and the launcher exits non-zero."""

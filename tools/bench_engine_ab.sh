@@ -4,7 +4,7 @@
 # by side.  usage: tools/bench_engine_ab.sh TAG
 tag=${1:?tag}
 for e in 0 1 0 1; do
-  tools/gpu_step.sh 300 ${tag}_e$e.log python -u bench.py --no-cpu-baseline --steps 3 --gemm-engine $e || exit 1
+  tools/gpu_step.sh 300 ${tag}_e$e.log python -u bench.py --full --no-cpu-baseline --steps 3 --gemm-engine $e || exit 1
   mv gpurun_out/${tag}_e$e.log gpurun_out/${tag}_e${e}_$(date +%s%N).log
 done
 python3 - "$tag" <<'PY'

@@ -9,7 +9,7 @@ if [ -n "$tf" ]; then
   $S 300 ${tag}_focus.log python -u -m pytest $tf -q --tb=short --timeout 120 --timeout-method thread || exit 1
 fi
 $S 600 ${tag}_pytest.log python -u -m pytest tests -m gpu -q --tb=short --timeout 300 --timeout-method thread || exit 1
-$S 400 ${tag}_bench.log python -u bench.py --no-cpu-baseline || exit 1
+$S 400 ${tag}_bench.log python -u bench.py --full --no-cpu-baseline || exit 1
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$tag -o run -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 > gpurun_out/${tag}_prof.log 2>&1 || exit 1
 f=$(find gpurun_out/prof_$tag -name '*kernel_stats.csv' | head -1)
 python3 tools/prof_summary.py "$f" 40 > gpurun_out/${tag}_kstats.txt

@@ -7,9 +7,9 @@ export TMPDIR=/tmp
 tag=${1:?tag}
 out=gpurun_out/$tag
 mkdir -p $out
-timeout -k 10 400 python -u bench.py > $out/bench.log 2>&1 || { tail -30 $out/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $out/bench.log 2>&1 || { tail -30 $out/bench.log; exit 1; }
 grep '^{' $out/bench.log > $out/bench.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python3 bench.py --no-cpu-baseline > $out/prof.log 2>&1 || { tail -20 $out/prof.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python3 bench.py --full --no-cpu-baseline > $out/prof.log 2>&1 || { tail -20 $out/prof.log; exit 1; }
 f=$(find $out/prof -name '*kernel_stats.csv' | head -1)
 cp "$f" $out/kernel_stats.csv
 python3 tools/prof_summary.py "$f" 40 > $out/kernel_stats.txt
